@@ -15,8 +15,13 @@ input, pixel buffer resident in HBM:
           (pt_comm_gather_frame / pt_render_sharded in include/ptgpu.h; ncclAllGather + ncclAllReduce on xGMI) and
           both inside the timed region. "scaling": "strong" (total work fixed as N grows).
           --mode frames is the other data-parallel axis (rank r renders progressive frame r of the 64-spp frame;
-          bit-identical to `-F N`); the default run reports it as the extra `weak_scaling_frames`, never as `value`.
+          bit-identical to `-F N`); a --full run reports it as the extra `weak_scaling_frames`, never as `value`.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line. --full adds everything else, untimed or timed apart
+from `value`: the multi-rank self-check, the other multi-GPU mode, the host-buffer contract, pipelined and progressive frames,
+the other workloads and BASELINE configurations, and the CPU baseline (each still switched off by its own --no-* option).
+--dump-outputs DIR writes what the last timed step computed (the frame and its ray count) as DIR/*.npy.
 """
 import argparse
 import glob
@@ -251,6 +256,25 @@ def roofline_block(kernel_name, kms, rays_launch, n_hitables, use_bvh, counters,
     return out
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, frame, rays):
+    """The arrays a caller of the timed path receives from its last step: the frame (H x W x 3 f32) and the ray count (as f64).
+    A frame that would not fit in DUMP_BYTES is written as a fixed, seeded sample of its pixels plus their flat indices."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "rays.npy"), np.array([rays], dtype=np.float64))
+    if frame.nbytes <= DUMP_BYTES // 2:
+        np.save(os.path.join(path, "frame.npy"), frame)
+        return
+    px = frame.reshape(-1, 3)
+    n = (DUMP_BYTES // 2) // (12 + 8)          # 12 bytes of colour + 8 of index per sampled pixel
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], n, replace=False))
+    np.save(os.path.join(path, "frame_sample.npy"), px[idx])
+    np.save(os.path.join(path, "frame_sample_pixels.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -263,12 +287,15 @@ def main():
     ap.add_argument("--mode", choices=["tiles", "frames"], default="tiles", help="how N > 1 GPUs are used (see above)")
     ap.add_argument("--depth", type=int, default=10)
     ap.add_argument("--bvh", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pipeline", action="store_true", help="N = 1: skip the extra measurement of overlapped independent frames")
-    ap.add_argument("--no-extras", action="store_true", help="skip every extra measurement (host-buffer contract, other multi-GPU mode)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-pipeline", action="store_true", help="with --full, N = 1: skip the extra measurement of overlapped independent frames")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip every extra measurement (host-buffer contract, other multi-GPU mode)")
     ap.add_argument("--no-overlap", action="store_true", help="N > 1: gather on the render stream through pt_render_sharded (no double buffering)")
     ap.add_argument("--cpu-secs", type=float, default=15.0)
+    ap.add_argument("--full", action="store_true", help="also run every check and extra measurement beside the headline (see above)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's frame and ray count as DIR/*.npy")
     args = ap.parse_args()
+    extras = args.full and not args.no_extras
 
     # ---- self-launch: `python bench.py --gpus N` without a launcher (nothing has touched the GPU yet)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and os.environ.get("PT_BENCH_FORCE_DIST") != "1":
@@ -442,8 +469,8 @@ def main():
         return float(t[0].item()), float(t[1].item()), float(t[2].item()), int(state["last"]["rays"].item())  # rays already summed over ranks
 
     self_check = None
-    if multi and os.environ.get("PT_BENCH_CHECK", "1") != "0":
-        # Untimed, before the warm-up, on EVERY multi-rank run: the frame the sharded / pipelined path delivers on this rank must equal
+    if multi and args.full and os.environ.get("PT_BENCH_CHECK", "1") != "0":
+        # Untimed, before the warm-up, on every multi-rank --full run: the frame the sharded / pipelined path delivers on this rank must equal
         # this rank's own unsharded render bit for bit, and the all-reduced ray count the unsharded frame's (scene.rs:90-93, 118-120).
         # The first run on a multi-GPU node is thereby also the first evidence for pt_comm.hip on real RCCL with more than one rank;
         # a mismatch on any rank ends the run with a non-zero exit code and no bench line.
@@ -485,13 +512,15 @@ def main():
         state["k"] = 0
 
     elapsed, kms, pms, rays_per_step = timed(args.mode, S, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:   # (before any extra reuses the buffer sets)
+        dump_outputs(args.dump_outputs, state["frame"].cpu().numpy(), rays_per_step)
     total_rays = rays_per_step * args.steps
     value = total_rays / 1e6 / elapsed
     ms_per_step = elapsed / args.steps * 1e3
     rays_this_launch = int(sets[0]["rays"].item()) if not multi else rays_per_step / N   # tiles: ~1/N of the frame's rays per rank
 
     other = None
-    if multi and not args.no_extras:   # the other decomposition, reported beside the main value
+    if multi and extras:   # the other decomposition, reported beside the main value
         k2 = max(2, min(args.steps, 5))
         m2, s2 = ("frames", 64) if args.mode == "tiles" else ("tiles", 256)
         el2, kms2, _, rays2 = timed(m2, s2, k2, 1)
@@ -504,7 +533,7 @@ def main():
     pipelined = None
     host_buffer = None
     progressive = None
-    if not multi and not args.no_extras and not hs.is_world:
+    if not multi and extras and not hs.is_world:
         # Extra, never `value`: the preview-window pattern (glium_window.rs: Scene::update(frame_num = 0, 1, 2, ...) blending
         # into ONE buffer). From the second frame of a view on, the work order comes from the rays each tile took in the frame
         # before (measured by the frame kernel itself), not from a measuring launch of its own. Same pixels either way.
@@ -534,7 +563,7 @@ def main():
                        "note": "Scene::update(frame_num = 1..%d) of one view accumulating into one buffer (the preview-window loop); "
                                "work ordered by the previous frame's measured rays per tile instead of a measuring launch of its own; "
                                "accumulated image bit-identical to the run that measures every frame anew" % kf}
-    if not multi and not args.no_extras:
+    if not multi and extras:
         # The reference's own contract -- Scene::update on a HOST buffer (offline.rs:27-34 times exactly this call), PCIe
         # inclusive. Reported at top level as `host_contract`; `value` stays the device-resident rate (the harness contract:
         # inputs resident in HBM when the timed region starts).
@@ -570,7 +599,7 @@ def main():
                                                  "new frame written pixel by pixel under the kernel, no copies at all")
         finally:
             ptgpu.buffer_unregister(hb)
-    if not multi and not args.no_pipeline and not args.no_extras:
+    if not multi and not args.no_pipeline and extras:
         # Extra figure, never `value`: independent frames back to back on two scene handles / two HIP streams, so the
         # tail of frame k (its last, serial pixels) and the measuring launch of frame k + 1 overlap. A single frame cannot
         # use this; a renderer producing a sequence of independent frames (animation, tiles of a bigger image) can.
@@ -602,7 +631,7 @@ def main():
                              "overlaps the start of the next); each frame is bit-identical to the single-frame result"}
 
     other_workloads = None
-    if not multi and not args.no_extras and args.preset == "random_spheres" and (W, H, S) == (1200, 800, 64) and not args.bvh:
+    if not multi and extras and args.preset == "random_spheres" and (W, H, S) == (1200, 800, 64) and not args.bvh:
         # Extra, never `value`: the other kernels of the path at the headline's frame size (a BVH world on the list kernel, the
         # general-world kernel on the reference's box / light presets), three frames of a never-seen view each after one warm-up.
         other_workloads = {}
@@ -625,7 +654,7 @@ def main():
             other_workloads[name] = {"value": int(ro.item()) / 1e6 / elo, "unit": "Mrays/s", "ms_per_frame": elo * 1e3, "kernel": so.last_kernel_choice()["name"]}
             del so, ho
     baseline_configs = None
-    if not multi and not args.no_extras and args.preset == "random_spheres" and (W, H, S) == (1200, 800, 64) and not args.bvh:
+    if not multi and extras and args.preset == "random_spheres" and (W, H, S) == (1200, 800, 64) and not args.bvh:
         # Extra, never `value`: the other BASELINE.json configurations on this one GPU, each at ITS frame size -- config 2 (aras
         # 1280x720x16), config 4's frame (random_spheres 1200x800x256; the multi-GPU run shards it) and config 5 (perlin_spheres,
         # 10 002 spheres, BVH, 1920x1080x128): one warm-up + three timed frames of a never-seen view each (bit 8192), the frame kernel's
@@ -713,7 +742,7 @@ def main():
         if self_check is not None:
             out["self_check"] = self_check
             out["config"]["sharded_equals_single"] = True
-        if N == 1 and not multi and not args.no_cpu_baseline:
+        if N == 1 and not multi and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.preset, W, H, S, depth, args.bvh, args.cpu_secs)
         print(json.dumps(out))
     if comm is not None:

@@ -209,8 +209,8 @@ def test_a_second_hip_runtime_in_the_process_is_reported_not_guessed(ptgpu):
 def test_pin_kit_runs_without_cargo_and_its_patch_still_applies(tmp_path):
     """Parity with the Rust binary is unpinned until someone with cargo runs ONE command (README "Pinning the oracle"). What can rot meanwhile
     is checked here: the script starts and explains itself without cargo, its PNG reader decodes what the product's writer encodes, the
-    expectations file holds the ten frames, and the 10-line patch that makes the reference dump its raw f32 frame still applies to the
-    reference tree (checked where /root/reference exists -- the build container; skipped on the GPU box)."""
+    expectations file holds the ten frames, and the 10-line patch that makes the reference dump its raw f32 frame still applies: to the
+    pre-image it carries itself, and to a reference checkout as well where PT_REFERENCE_TREE names one."""
     tool = os.path.join(ROOT, "tools", "pin_against_rust.py")
     out = subprocess.run([sys.executable, tool, "--help"], capture_output=True, text=True, timeout=60)
     assert out.returncode == 0 and "cargo" in out.stdout.lower(), out.stdout + out.stderr
@@ -234,12 +234,36 @@ def test_pin_kit_runs_without_cargo_and_its_patch_still_applies(tmp_path):
     f.write_bytes(png)
     got = pin.png_rgb8(str(f))
     assert np.array_equal(np.frombuffer(got, np.uint8).reshape(5, 7, 3), rgb)
-    ref = "/root/reference"
     patch = os.path.join(ROOT, "tools", "pin", "offline_dump_f32.patch")
     assert os.path.exists(patch)
-    if not os.path.isdir(os.path.join(ref, "src")):
-        pytest.skip("no reference tree here: the patch is checked in the build container")
-    copy = tmp_path / "ref"
-    shutil.copytree(ref, copy, ignore=shutil.ignore_patterns("target", ".git"))
-    chk = subprocess.run(["git", "apply", "--check", "--verbose", patch], cwd=copy, capture_output=True, text=True)
+    # The reference tree is not part of this repository: the file the patch edits is rebuilt from the patch's own pre-image (context and
+    # removed lines at the line numbers its hunk headers name, blank lines elsewhere). The patch must apply to that file cleanly and leave
+    # exactly its post-image there, so an edit that breaks a hunk's counts, offsets or context is caught without the reference.
+    text = open(patch).read()
+    target = re.search(r"^\+\+\+ b/(\S+)$", text, flags=re.M).group(1)
+    hunks = re.findall(r"^@@ -(\d+),(\d+) \+(\d+),(\d+) @@[^\n]*\n((?:[ +-][^\n]*\n?)*)", text, flags=re.M)
+    assert target == "src/offline.rs" and hunks, text[:200]
+    before, after = [], {}
+    for old_start, old_len, new_start, new_len, body in hunks:
+        lines = body.splitlines()
+        old = [l[1:] for l in lines if l[:1] in " -"]
+        new = [l[1:] for l in lines if l[:1] in " +"]
+        assert (len(old), len(new)) == (int(old_len), int(new_len)), "hunk @@ -%s,%s +%s,%s @@ miscounts its lines" % (old_start, old_len, new_start, new_len)
+        before += [""] * (int(old_start) - 1 - len(before)) + old
+        after[int(new_start)] = new
+    src = tmp_path / "pre" / target
+    src.parent.mkdir(parents=True)
+    src.write_text("\n".join(before) + "\n")
+    chk = subprocess.run(["git", "apply", "--verbose", patch], cwd=tmp_path / "pre", capture_output=True, text=True)
     assert chk.returncode == 0, chk.stdout + chk.stderr
+    got = src.read_text().splitlines()
+    for start, new in after.items():
+        assert got[start - 1:start - 1 + len(new)] == new
+    assert any("PT_DUMP_F32" in l for l in got)
+    # where a checkout of the reference is at hand, the patch is also checked against it (PT_REFERENCE_TREE=<checkout>)
+    ref = os.environ.get("PT_REFERENCE_TREE")
+    if ref:
+        copy = tmp_path / "ref"
+        shutil.copytree(ref, copy, ignore=shutil.ignore_patterns("target", ".git"))
+        chk = subprocess.run(["git", "apply", "--check", "--verbose", patch], cwd=copy, capture_output=True, text=True)
+        assert chk.returncode == 0, chk.stdout + chk.stderr

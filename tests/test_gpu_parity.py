@@ -2056,7 +2056,7 @@ def test_device_pow5_vs_host_powf_mismatch_rate(ptgpu, oracle):
 
 def test_bench_sharded_path_self_check():
     """bench.py's N > 1 path (BASELINE config 4 through pt_comm_gather_frame, three buffer sets, exchange on a second stream)
-    on the one rank a 1-GPU box can form, at a reduced sample count: every multi-rank run first checks, untimed, that the gathered
+    on the one rank a 1-GPU box can form, at a reduced sample count: every multi-rank --full run first checks, untimed, that the gathered
     frame equals the rank's own full render bit for bit (and says so in its line; a mismatch exits non-zero); the JSON line must say
     strong scaling and carry the roofline block."""
     import json
@@ -2065,7 +2065,7 @@ def test_bench_sharded_path_self_check():
     env.pop("PT_BENCH_CHECK", None)   # (the check is on by default)
     for extra, spp in (([], "16"), (["--no-overlap"], "8")):   # (16 spp: the shard renders as two launches; 8: as one)
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--samples", spp,
-                              "--no-extras", "--no-cpu-baseline"] + extra, env=env, capture_output=True, text=True, timeout=600)
+                              "--full", "--no-extras", "--no-cpu-baseline"] + extra, env=env, capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
         assert "[bench check] tiles frame over 1 rank(s) == single-GPU frame" in out.stderr
         line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -2082,7 +2082,7 @@ def test_bench_multi_rank_path_on_one_gpu_behind_the_cross_process_test_double(r
     --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N): rank 0's unique id travels over the launcher's process
     group, every rank creates its pt_comm, renders its rows of BASELINE config 4's frame (at a reduced sample count), the shards are
     exchanged through pt_comm_gather_frame (on a second stream) or pt_render_sharded -- and the script's self-check, which runs before the
-    warm-up on every multi-rank run, finds the gathered frame on EVERY rank equal to that rank's own unsharded render and the reduced ray
+    warm-up on every multi-rank --full run, finds the gathered frame on EVERY rank equal to that rank's own unsharded render and the reduced ray
     count equal to the frame's. One GPU only, so: all ranks on device 0, the launcher's group over gloo, and the C ABI's RCCL pinned
     (PTGPU_RCCL_LIBRARY) to tests/mock_rccl/mock_rccl_xproc.hip, which moves the data through shared memory. Real RCCL stays out of it."""
     import json
@@ -2094,7 +2094,7 @@ def test_bench_multi_rank_path_on_one_gpu_behind_the_cross_process_test_double(r
     env = dict(os.environ, PT_BENCH_ONE_DEVICE="1", PT_BENCH_BACKEND="gloo", PTGPU_RCCL_LIBRARY=lib)
     env.pop("PT_BENCH_CHECK", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1", "--master-port", str(29540 + ranks),
-           os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--samples", "16", "--no-extras", "--no-cpu-baseline"] + extra
+           os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--samples", "16", "--full", "--no-extras", "--no-cpu-baseline"] + extra
     try:
         out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     finally:
@@ -2113,11 +2113,11 @@ def test_bench_multi_rank_path_on_one_gpu_behind_the_cross_process_test_double(r
 
 
 def test_bench_default_line_keeps_the_contract():
-    """The one JSON line of `python bench.py` (N = 1): BASELINE's metric on BASELINE's workload, every fraction of the roofline
+    """The one JSON line of `python bench.py --full` (N = 1): BASELINE's metric on BASELINE's workload, every fraction of the roofline
     block <= 1, the extras present and self-consistent (bench.py asserts that each extra reproduces the headline frame)."""
     import json
     import subprocess
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -2142,3 +2142,28 @@ def test_bench_default_line_keeps_the_contract():
     c5 = bc["config 5: perlin_spheres 1920x1080 128spp BVH"]
     assert c5["hitables"] == 10002 and 0.0 < frac_of(c5["roofline"]) <= 1.0
 
+
+
+def test_bench_plain_line_times_the_headline_alone_and_dumps_its_last_frame(ptgpu, pthost, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: the line keeps the headline's keys, carries none of the checks and
+    extras --full adds, and --dump-outputs writes what the last timed step computed -- the frame and its ray count -- which equal a
+    render of the same frame through the host entry point, bit for bit."""
+    import json
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["metric"] == "Mrays/sec, random_spheres 1200x800 64spp" and d["unit"] == "Mrays/s" and d["n_gpus"] == 1
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - d["config"]["rays_per_step"] / 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    for key in ("host_contract", "pipelined_frames", "progressive_view", "other_workloads_same_frame_size", "baseline_configs", "cpu_baseline", "self_check"):
+        assert key not in d, key
+    assert sorted(os.listdir(tmp_path / "dump")) == ["frame.npy", "rays.npy"]
+    frame, rays = np.load(tmp_path / "dump" / "frame.npy"), np.load(tmp_path / "dump" / "rays.npy")
+    assert frame.dtype == np.float32 and frame.shape == (800, 1200, 3) and rays.dtype == np.float64
+    assert rays.tolist() == [d["config"]["rays_per_step"]]
+    W, H, S = 1200, 800, 64
+    hs = pthost.HostScene("random_spheres", W, H, samples=S, device=0)
+    ref = np.zeros((H, W, 3), np.float32)
+    assert hs.device_scene().update(ptgpu.PtParams(W, H, S, 10, 0, 0), hs.camera, 0, ref) == rays[0]
+    assert np.array_equal(frame, ref)

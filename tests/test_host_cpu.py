@@ -332,6 +332,30 @@ def test_bench_binds_its_counters_to_the_build_and_reads_the_cpu_quota(ptgpu):
     assert (quota is None or 0 < quota <= (os.cpu_count() or 1)) and isinstance(where, str) and where
 
 
+def test_bench_dump_outputs_caps_its_size_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: a frame within the cap is written whole; a larger one as the same seeded sample of pixels (plus their flat
+    indices, float64) on every run, within the cap."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    frame = np.random.default_rng(1).random((60, 90, 3), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "whole"), frame, 12345)
+    assert np.array_equal(np.load(tmp_path / "whole" / "frame.npy"), frame) and np.load(tmp_path / "whole" / "rays.npy").tolist() == [12345.0]
+    bench.DUMP_BYTES = frame.nbytes      # (the frame no longer fits in half of it)
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("sample%d" % k)
+        bench.dump_outputs(str(d), frame, 12345)
+        assert sorted(os.listdir(d)) == ["frame_sample.npy", "frame_sample_pixels.npy", "rays.npy"]
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= bench.DUMP_BYTES
+        px, idx = np.load(d / "frame_sample.npy"), np.load(d / "frame_sample_pixels.npy")
+        assert px.dtype == np.float32 and idx.dtype == np.float64 and len(idx) > 0 and np.all(np.diff(idx) > 0)
+        assert np.array_equal(px, frame.reshape(-1, 3)[idx.astype(np.int64)])
+        runs.append(idx)
+    assert np.array_equal(runs[0], runs[1])
+
+
 def test_product_never_references_the_oracle():
     """The product path must not import, link or call anything under oracle/."""
     pkg = os.path.join(ROOT, "pathtrace-rs_amd")
